@@ -11,6 +11,12 @@ Workload (configs[1]): 46 Mbp chr21-sized synthetic sequence per GPU.  One step 
 over bases already resident in HBM.  Weak scaling: rank r owns its own contiguous,
 1 Mi-aligned 46 Mbp shard of the genome; value = bases of all ranks / step time (max over
 ranks).  Launched as `python bench.py` (N=1) or via torch.distributed.run for N>1.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (with
+--dump-outputs DIR the last timed step's results as DIR/<name>.npy first).  --full adds the
+legs that take runs of their own: the CPU baseline, the comparison with the oracle's
+committed results (fingerprint), the Baum-Welch iteration leg, the cold-cache steps and the
+C3 leg with the count kernel's roofline; their entries of the result line are null without it.
 """
 import argparse
 import json
@@ -315,6 +321,53 @@ def sha256_hex(*arrays):
     for a in arrays:
         h.update(np.ascontiguousarray(a).view(np.uint8).tobytes())
     return h.hexdigest()
+
+
+DUMP_BLOCK = 1 << 17           # --dump-outputs: the path per base in DUMP_BLOCKS seeded blocks
+DUMP_BLOCKS = 64               # of DUMP_BLOCK bases each (32 MB as float32)
+DUMP_POP = 4096                # and its island-state count per DUMP_POP bases, every base
+
+
+def dump_outputs(dirname, estep, counts, sign_words, scores, islands, nbases):
+    """--dump-outputs: one step's results as <dirname>/<name>.npy, float32 / float64 (every
+    integer here is exact in float64), for comparing two builds output for output:
+      estep            the E-step's 105 expected counts (the last is the log-likelihood)
+      labelled_counts  the 124 labelled counts
+      scores           the Viterbi score of every decode chunk
+      islands          one row per island record: beg1, end1, len, chunk, cg, oe
+      path_sample      the decoded path's island-state bit per base: every base up to
+                       DUMP_BLOCKS * DUMP_BLOCK, else DUMP_BLOCKS blocks of DUMP_BLOCK bases
+                       (drawn once from SEED: the same blocks in every run), in genome order
+      path_blocks      the first base of each of those blocks
+      path_popcount    island-state bases per DUMP_POP bases of the whole path
+    (several ranks: rank 0's path and scores, every rank's island records, merged counts)."""
+    os.makedirs(dirname, exist_ok=True)
+    by = np.ascontiguousarray(sign_words).view(np.uint8)[: (nbases + 7) // 8]
+    if nbases % 8:   # (bits past the last base are not results)
+        by = by.copy()
+        by[-1] &= (1 << nbases % 8) - 1
+    nblk = nbases // DUMP_BLOCK
+    if nblk <= DUMP_BLOCKS:
+        blocks = np.zeros(1, np.int64)
+        sample = np.unpackbits(by, bitorder="little")[:nbases]
+    else:
+        blocks = np.sort(np.random.default_rng(SEED).choice(nblk, DUMP_BLOCKS, replace=False))
+        blocks = blocks.astype(np.int64) * DUMP_BLOCK
+        sample = np.concatenate([np.unpackbits(by[b // 8:(b + DUMP_BLOCK) // 8], bitorder="little")
+                                 for b in blocks])
+    ones = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).astype(np.uint8)
+    pc = ones[by]
+    pc = np.concatenate([pc, np.zeros(-len(pc) % (DUMP_POP // 8), np.uint8)])
+    isl = np.stack([islands[f].astype(np.float64) for f in islands.dtype.names], axis=1) \
+        if len(islands) else np.zeros((0, len(islands.dtype.names)), np.float64)
+    for name, a in (("estep", np.asarray(estep, np.float64)),
+                    ("labelled_counts", np.asarray(counts).astype(np.float64)),
+                    ("scores", np.asarray(scores, np.float64)),
+                    ("islands", isl),
+                    ("path_sample", sample.astype(np.float32)),
+                    ("path_blocks", blocks.astype(np.float64)),
+                    ("path_popcount", pc.reshape(-1, DUMP_POP // 8).sum(1, dtype=np.float64))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def oracle_fixture(name, seed, start, nbases):
@@ -703,7 +756,7 @@ def run_c3(args, world, rank, local, dist, backend, dev, emit=True):
     # decode chunks' paths and scores, one MIN all-reduce; rank 0 the gathered records and the
     # merged counts / E-step
     chk = None
-    if fx is not None:
+    if fx is not None and args.full:
         pth, scs = chunks_match(fx, so.cpu().numpy().view(np.uint32), score.cpu().numpy(),
                                 pl.d0, pl.d1)
         chk = torch.tensor([int(pth), int(scs)], dtype=torch.int64, device=dev)
@@ -722,9 +775,13 @@ def run_c3(args, world, rank, local, dist, backend, dev, emit=True):
         else:
             recs = iout[last][:counts[0]].cpu().numpy().reshape(-1)
         lm = lmerged.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, emerged.cpu().numpy()[:105], lm,
+                         so.cpu().numpy()[:D.words32(de_n)], score.cpu().numpy()[:pl.d1 - pl.d0],
+                         recs.view(D._lib.ISLAND_DTYPE), de_n)
         fp = {"records_sha256": sha256_hex(recs), "counts_sha256": sha256_hex(lm),
-              "islands": int(sum(counts)), "oracle_match": None}
-        if fx is not None:
+              "islands": int(sum(counts)), "oracle_match": None} if args.full else None
+        if fx is not None and args.full:
             from cpgisland_amd import fingerprint as F
             ok, rel = F.estep_close(emerged.cpu().numpy()[:105], fx["train"]["estep_hex"],
                                     fx["train"]["estep_bound_hex"])
@@ -787,7 +844,7 @@ def run_c3(args, world, rank, local, dist, backend, dev, emit=True):
         if pmc:
             out["roofline"]["traffic"] = pmc["traffic_bytes"]
             out["roofline"]["traffic_source"] = "stored PMC profile, not this run: " + pmc["source"]
-        if world == 1:   # the count kernel alone over the same HBM-resident genome
+        if world == 1 and args.full:   # the count kernel alone over the same HBM-resident genome
             out["roofline_count"] = count_leg(ctx, bufs[0][0][tr_o // 16:], bufs[0][1][tr_o // 32:],
                                               tr_n)
         if emit:
@@ -900,7 +957,23 @@ def main():
                          "behind a 1 GiB scratch write (cold Infinity Cache), reported as "
                          "cold_cache beside the headline with the same joined steps warm "
                          "(0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg and check: the CPU "
+                         "baseline, the comparison with the oracle's committed results "
+                         "(fingerprint), the Baum-Welch iteration leg (--bw-iters), the cold-cache "
+                         "steps (--cold-steps), the C3 leg with the count kernel's roofline "
+                         "(--c3-steps).  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the result line with those entries null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's results (E-step and "
+                         "labelled counts, Viterbi path and scores, island records) as "
+                         "DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline figure alone
+        args.bw_iters = args.cold_steps = args.c3_steps = 0
+        args.no_cpu_baseline = True
+    if args.dump_outputs and args.decode_split > 1:
+        sys.exit("bench.py: --dump-outputs needs --decode-split 1 (records spread over parts)")
     if args.flush_mb:
         args.serial = True   # the flushed step time is the sum of isolated phase times
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1232,13 +1305,19 @@ def main():
     # the last timed step's results (its lane's buffers) against the oracle's over the whole
     # shard (rank 0's shard is the digested C2 genome); before the BW leg reuses the buffers
     fingerprint = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_outputs):
         kl = nwarm + args.steps - 1
         ln = lanes[kl % nlanes]
         _, _, d_so, d_score, d_iout, d_icnt = ln["dec"][kl % ndl]
         _, ecnt_l, lcnt_l = ln["recs"][kl % len(ln["recs"])]
-        fingerprint = c2_fingerprint(fx, d_so, d_score, d_iout, d_icnt, ecnt_l, lcnt_l, ndec,
-                                     nsplit)
+        if args.dump_outputs:   # (the path of the whole decode chunks: the rest is not decoded)
+            dump_outputs(args.dump_outputs, ecnt_l.cpu().numpy()[:105], lcnt_l.cpu().numpy(),
+                         d_so.cpu().numpy()[:D.words32(ndec * DECODE)],
+                         d_score.cpu().numpy()[:ndec], D.islands_to_numpy(d_iout, d_icnt),
+                         ndec * DECODE)
+        if args.full:
+            fingerprint = c2_fingerprint(fx, d_so, d_score, d_iout, d_icnt, ecnt_l, lcnt_l,
+                                         ndec, nsplit)
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -1263,6 +1342,7 @@ def main():
         import copy
         a3 = copy.copy(args)
         a3.steps, a3.warmup, a3.bases = args.c3_steps, 3, C3_BASES
+        a3.dump_outputs = None
         c3_leg = run_c3(a3, 1, 0, local, False, backend, dev, emit=False)
         if c3_leg is not None:
             c3_leg = {k: c3_leg[k] for k in ("value", "unit", "ms_per_step", "steps",

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; OUT=gpurun_out/${TAG:-ab_lanes3}; mkdir -p 
 for r in 1 2; do
   for v in ${VARS:-"cus192:" "cus224:--train-cus 224"}; do
     n=${v%%:*}; f=${v#*:}
-    timeout -k 10 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --c3-steps 0 --cold-steps 0 $f \
+    timeout -k 10 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --c3-steps 0 --cold-steps 0 $f \
       > $OUT/${n}_$r.json 2> $OUT/${n}_$r.err || { tail -5 $OUT/${n}_$r.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$OUT/${n}_$r.json').read().strip().splitlines()[-1])

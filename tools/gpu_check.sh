@@ -18,13 +18,13 @@ if [ -n "$EXTRA" ]; then
   tail -2 $OUT/extra.jsonl
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { tail -5 $OUT/bench_driver.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { tail -5 $OUT/bench_driver.err; exit 1; }
   python3 tools/bench_summary.py $OUT/bench_driver.json
 fi
 if [ "${PROF:-0}" = 1 ]; then
   export TMPDIR=/tmp
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o prof \
-    -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err) || { tail -5 $OUT/bench_prof.err; exit 1; }
+    -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err) || { tail -5 $OUT/bench_prof.err; exit 1; }
   find $OUT/prof -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_prof.csv \;
   python3 tools/bench_summary.py $OUT/bench_prof.json
 fi

@@ -4,7 +4,7 @@
 # C3 fingerprints must equal the N = 1 leg's.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; R=$(pwd); OUT=$R/gpurun_out/${TAG:-final}; mkdir -p $OUT
 bash tools/gpu_check.sh || exit 1
-CPG_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 2 --settle-ms 0 \
+CPG_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 5 --warmup 2 --settle-ms 0 \
     > $OUT/c3_gloo2.out 2> $OUT/c3_gloo2.err || { tail -20 $OUT/c3_gloo2.err; exit 1; }
 grep '^{' $OUT/c3_gloo2.out > $OUT/c3_gloo2.json
 python3 - <<PY

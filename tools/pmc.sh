@@ -5,7 +5,7 @@
 #   PMC_NAME  output directory under gpurun_out/ (default pmc)
 #   PMC_ARGS  bench.py arguments (default: the C2 step, serial)
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; R=$(pwd); OUT=$R/gpurun_out/${PMC_NAME:-pmc}; mkdir -p $OUT
-ARGS=${PMC_ARGS:---steps 2 --warmup 1 --no-cpu-baseline --serial --c3-steps 0 --cold-steps 0 --settle-ms 0}
+ARGS=${PMC_ARGS:---full --steps 2 --warmup 1 --no-cpu-baseline --serial --c3-steps 0 --cold-steps 0 --settle-ms 0}
 cd /tmp && export TMPDIR=/tmp
 run() {
   local name=$1; shift

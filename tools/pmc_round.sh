@@ -7,7 +7,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; R=$(pwd)
 PMC_NAME=pmc bash tools/pmc.sh || exit 1
 python tools/pmc_summary.py gpurun_out/pmc gpurun_out/pmc_latest.json 46000000 "bench.py --serial (C2)" > gpurun_out/pmc_summary.txt || exit 1
-PMC_NAME=pmc_c3 PMC_ARGS="--workload c3 --steps 2 --warmup 1 --no-cpu-baseline --settle-ms 0" bash tools/pmc.sh || exit 1
+PMC_NAME=pmc_c3 PMC_ARGS="--full --workload c3 --steps 2 --warmup 1 --no-cpu-baseline --settle-ms 0" bash tools/pmc.sh || exit 1
 python tools/pmc_summary.py gpurun_out/pmc_c3 gpurun_out/pmc_c3.json 3100000000 "bench.py --workload c3 (two streams)" > gpurun_out/pmc_c3_summary.txt || exit 1
 OUT=$R/gpurun_out/pmc_count; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

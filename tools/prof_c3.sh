@@ -9,6 +9,6 @@ find $OUT/dec -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_decode_c3.
 cat $OUT/decode_c3.json
 python3 tools/kstats.py $OUT/kernel_stats_decode_c3.csv 2>/dev/null | head -20 || head -20 $OUT/kernel_stats_decode_c3.csv
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --bw-iters 0 > $OUT/c3_$i.json 2> $OUT/c3_$i.err || { tail -5 $OUT/c3_$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --bw-iters 0 > $OUT/c3_$i.json 2> $OUT/c3_$i.err || { tail -5 $OUT/c3_$i.err; exit 1; }
   python3 tools/bench_summary.py $OUT/c3_$i.json
 done
