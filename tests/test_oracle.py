@@ -92,27 +92,36 @@ def test_viterbi_two_state_collapse_bitwise_long():
     assert np.array_equal(sg, (st < 4).astype(np.uint8)) and b2 == best
 
 
-def test_viterbi_brute_force_small():
-    """Enumerate all 2^T sign paths (T <= 12): the argmax value equals the Viterbi score."""
+def brute_force_check(model, obs):
+    """Enumerate all 2^T sign paths of `obs` under the flat `model`: the argmax value equals
+    the oracle's Viterbi score, and the decoded path scores the optimum."""
     import itertools
     import math
+    pi, a, _ = co.model_split(np.asarray(model, np.float64))
+    pi, a = pi.tolist(), a.tolist()
+    obs = [int(o) for o in obs]
+    T = len(obs)
+    st, best = co.viterbi8(model, np.array(obs, np.uint8))
+    bestv = -math.inf
+    for signs in itertools.product((0, 1), repeat=T):
+        s = [o + (0 if g else 4) for o, g in zip(obs, signs)]
+        v = math.log(pi[s[0]])
+        for t in range(1, T):
+            v += math.log(a[s[t - 1]][s[t]])
+        bestv = max(bestv, v)
+    assert abs(bestv - best) <= 1e-12 * abs(best)
+    # the decoded path scores the optimum
+    v = math.log(pi[st[0]])
+    for t in range(1, T):
+        v += math.log(a[st[t - 1]][st[t]])
+    assert abs(v - best) <= 1e-12 * abs(best)
+
+
+def test_viterbi_brute_force_small():
+    """Enumerate all 2^T sign paths (T <= 12): the argmax value equals the Viterbi score."""
     rng = np.random.default_rng(3)
     for T in (2, 5, 9, 12):
-        obs = rng.integers(0, 4, T).tolist()
-        st, best = co.viterbi8(m0(), np.array(obs, np.uint8))
-        bestv = -math.inf
-        for signs in itertools.product((0, 1), repeat=T):
-            s = [o + (0 if g else 4) for o, g in zip(obs, signs)]
-            v = math.log(pr.INITIAL_PI[s[0]])
-            for t in range(1, T):
-                v += math.log(pr.INITIAL_A[s[t - 1]][s[t]])
-            bestv = max(bestv, v)
-        assert abs(bestv - best) <= 1e-12 * abs(best)
-        # the decoded path scores the optimum
-        v = math.log(pr.INITIAL_PI[st[0]])
-        for t in range(1, T):
-            v += math.log(pr.INITIAL_A[st[t - 1]][st[t]])
-        assert abs(v - best) <= 1e-12 * abs(best)
+        brute_force_check(m0(), rng.integers(0, 4, T).tolist())
 
 
 def test_kat_cg_repeat_decodes_plus_and_at_repeat_minus():
