@@ -78,6 +78,9 @@ SIGNATURES = {
     "cpg_islands_d": [_P, _P, _P, _I64, _I64, _P, _I64, _P, _P],
     "cpg_islands_at_d": [_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _P],
     "cpg_decode_d": [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P],
+    "cpg_posterior_d": [_P, _P, _P, _I64, _I64, _P, _P, _P, _P],
+    "cpg_island_confidence_d": [_P, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _P],
+    "cpg_posterior_states": [_P, _P, _P, _I64, _P, _P],
     "cpg_count_labelled": [_P, _P, _P, _I64, _I64, _P],
     "cpg_bw_estep": [_P, _P, _P, _I64, _I64, _P],
     "cpg_viterbi": [_P, _P, _P, _I64, _I64, _P, _P],

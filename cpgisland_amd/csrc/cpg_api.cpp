@@ -253,11 +253,21 @@ static int reserve_lengths(cpg_ctx* ctx, int64_t nbases, int flags, int64_t c_lo
             gen = std::max(gen, vitg_ws_bytes(nbases / C, C));
         if ((rc = ws_get(ctx, WS_VGEN, gen, &p))) return rc;
     }
+    if (flags & CPG_RESERVE_POSTERIOR) {
+        // the posterior pass: several chunks of a multiple of 4,096, or the whole input as one
+        // chunk (cpg_posterior_states)
+        size_t post = posterior_ws_bytes(1, std::max<int64_t>(nbases, 1));
+        for (int64_t C = c_lo; C <= c_hi; C += c_step)
+            if (C % 4096 == 0) post = std::max(post, posterior_ws_bytes(nbases / C + 1, C));
+        if ((rc = ws_get(ctx, WS_POST, post, &p))) return rc;
+    }
     return CPG_OK;
 }
 
+static constexpr int kReserveFlags = CPG_RESERVE_GENERAL | CPG_RESERVE_POSTERIOR;
+
 int cpg_reserve_ex(cpg_ctx* ctx, int64_t nbases, int flags) {
-    if (!ctx || nbases < 0 || (flags & ~CPG_RESERVE_GENERAL))
+    if (!ctx || nbases < 0 || (flags & ~kReserveFlags))
         return set_error(CPG_E_INVALID, "bad argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     CPG_HIP(hipSetDevice(ctx->device));
@@ -270,7 +280,7 @@ int cpg_reserve_ex(cpg_ctx* ctx, int64_t nbases, int flags) {
 }
 
 int cpg_reserve_chunk(cpg_ctx* ctx, int64_t nbases, int64_t chunk_len, int flags) {
-    if (!ctx || nbases < 0 || chunk_len <= 0 || chunk_len % 32 || (flags & ~CPG_RESERVE_GENERAL))
+    if (!ctx || nbases < 0 || chunk_len <= 0 || chunk_len % 32 || (flags & ~kReserveFlags))
         return set_error(CPG_E_INVALID, "bad argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     CPG_HIP(hipSetDevice(ctx->device));
@@ -317,6 +327,10 @@ int cpg_sync(cpg_ctx* ctx, void* stream) {
                              "viterbi (general model): the decoded path visits states that are "
                              "not their position's base (a dead end of zero transitions); sign "
                              "bits cannot carry it: use cpg_viterbi_states_d (status 0x%x)", st);
+        if (st & ST_CONF_RANGE)
+            return set_error(CPG_E_INVALID,
+                             "island confidence: a record's chunk or span lies outside the "
+                             "posterior buffer; its confidence is NaN (status 0x%x)", st);
         if (st == ST_CONTIG_LAYOUT)
             return set_error(CPG_E_INVALID,
                              "contig batch: a contig breaks the layout contract (offset %% 64, "
@@ -590,6 +604,47 @@ int cpg_train_pass_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* d_pac
     return CPG_OK;
 }
 
+int cpg_posterior_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* d_packed,
+                    int64_t nbases, int64_t chunk_len, float* d_post, uint32_t* d_sign_out,
+                    double* d_loglik, void* stream) {
+    if (!ctx || !model) return set_error(CPG_E_INVALID, "null argument");
+    int rc = check_layout(d_packed, nbases, chunk_len);
+    if (rc) return rc;
+    const int64_t nch = nbases / chunk_len;
+    if (nch > 1 && (chunk_len % 4096 || chunk_len > CPG_DECODE_CHUNK))
+        return set_error(CPG_E_INVALID,
+                         "posterior chunk_len must be a multiple of 4096, <= 1048576, for >1 chunk");
+    if ((rc = model_check_deterministic(model))) return rc;
+    if (!aligned16(d_post) || !aligned16(d_sign_out))
+        return set_error(CPG_E_INVALID, "post / sign_out not 16-byte aligned");
+    if (nch == 0 || (!d_post && !d_sign_out && !d_loglik)) return CPG_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CPG_HIP(hipSetDevice(ctx->device));
+    void* ws;
+    if ((rc = ws_get(ctx, WS_POST, posterior_ws_bytes(nch, chunk_len), &ws))) return rc;
+    const double2* gtab = nullptr;
+    if ((rc = est_tables(ctx, model, &gtab))) return rc;
+    CPG_HIP(launch_posterior(*model, gtab, d_packed, nch, chunk_len, ws, d_post, d_sign_out,
+                             d_loglik, pick(ctx, stream)));
+    return CPG_OK;
+}
+
+int cpg_island_confidence_d(cpg_ctx* ctx, const float* d_post, int64_t nbases, int64_t chunk_len,
+                            int64_t first_chunk, const cpg_island* d_islands,
+                            const int64_t* d_count, int64_t cap, float* d_conf, void* stream) {
+    if (!ctx || !d_count || cap < 0 || (cap > 0 && (!d_islands || !d_conf)) ||
+        (!d_post && nbases > 0))
+        return set_error(CPG_E_INVALID, "null argument");
+    if (nbases < 0 || chunk_len <= 0)
+        return set_error(CPG_E_INVALID, "nbases=%lld chunk_len=%lld", (long long)nbases,
+                         (long long)chunk_len);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CPG_HIP(hipSetDevice(ctx->device));
+    CPG_HIP(launch_island_conf(d_post, nbases / chunk_len, chunk_len, first_chunk, d_islands,
+                               d_count, cap, d_conf, ctx->d_status, pick(ctx, stream)));
+    return CPG_OK;
+}
+
 int cpg_merge_train_d(cpg_ctx* ctx, const void* d_gathered, int world, double* d_estep,
                       int64_t* d_counts, void* stream) {
     if (!ctx || !d_gathered || !d_estep || !d_counts || world < 1)
@@ -738,6 +793,46 @@ int cpg_decode_states(cpg_ctx* ctx, const cpg_model* model, const int32_t* obs, 
         const bool plus = (sign[i >> 5] >> (i & 31)) & 1u;
         states_out[i] = degen ? 0 : obs[i] + (plus ? 0 : 4);
     }
+    return CPG_OK;
+}
+
+// Posterior decoding of one observation array (the counterpart of cpg_decode_states): the
+// array is one chunk of n positions; packed words and results go through the context's pinned
+// buffers (the caller's memory is never page-locked).
+int cpg_posterior_states(cpg_ctx* ctx, const cpg_model* model, const int32_t* obs, int64_t n,
+                         float* post_out, double* loglik) {
+    if (!ctx || !model || !obs || (!post_out && !loglik))
+        return set_error(CPG_E_INVALID, "null argument");
+    if (n < 1) return set_error(CPG_E_INVALID, "empty observation array");
+    const size_t nw = (size_t)(n + 15) / 16, post_bytes = ((size_t)n * 4 + 7) & ~(size_t)7;
+    void *hp, *ho, *dp, *dpost, *dll;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        CPG_HIP(hipSetDevice(ctx->device));
+        CPG_TRY(pin_get(ctx, 0, nw * 4 + 16, &hp));
+        CPG_TRY(pin_get(ctx, 1, post_bytes + 8, &ho));
+        uint32_t* pw = static_cast<uint32_t*>(hp);
+        std::memset(pw, 0, nw * 4);
+        for (int64_t i = 0; i < n; ++i) {
+            if (obs[i] < 0 || obs[i] > 3)
+                return set_error(CPG_E_INVALID,
+                                 "observation %lld = %d not in 0..3 (reference: "
+                                 "ArrayIndexOutOfBoundsException)", (long long)i, obs[i]);
+            pw[i >> 4] |= (uint32_t)obs[i] << ((i & 15) * 2);
+        }
+        CPG_TRY(stage_in(ctx, WS_IN0, hp, nw * 4, &dp));
+        CPG_TRY(ws_get(ctx, WS_OUT0, post_bytes + 16, &dpost));
+        CPG_TRY(ws_get(ctx, WS_OUT1, 16, &dll));
+    }
+    CPG_TRY(cpg_posterior_d(ctx, model, (const uint32_t*)dp, n, n, post_out ? (float*)dpost : nullptr,
+                            nullptr, (double*)dll, ctx->stream));
+    if (post_out)
+        CPG_HIP(hipMemcpyAsync(ho, dpost, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CPG_HIP(hipMemcpyAsync(static_cast<unsigned char*>(ho) + post_bytes, dll, 8,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    CPG_TRY(cpg_sync(ctx, ctx->stream));
+    if (post_out) std::memcpy(post_out, ho, (size_t)n * 4);
+    if (loglik) std::memcpy(loglik, static_cast<unsigned char*>(ho) + post_bytes, 8);
     return CPG_OK;
 }
 

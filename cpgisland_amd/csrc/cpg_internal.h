@@ -35,6 +35,8 @@ enum : uint32_t {
     // another workgroup any more)
     ST_GEN_NOT_SIGN = 1u << 6,       // general-model path: a state is not its base's (the path
                                      // is not representable as sign bits)
+    ST_CONF_RANGE = 1u << 7,         // island confidence: a record's chunk or span lies outside
+                                     // the posterior buffer (its confidence is NaN)
 };
 
 // ---- Viterbi constants (host-computed, shared by every kernel) ---------------------
@@ -151,7 +153,10 @@ enum { WS_COUNT = 0, WS_VIT = 1, WS_ISL = 2, WS_EST = 3, WS_IN0 = 4, WS_IN1 = 5,
        // allocated, reset by the workgroup that completes a chunk), so a slot of their own
        WS_IDONE = 18,
        // the general-model Viterbi (backpointer ballots, states, state-packed words)
-       WS_VGEN = 19, WS_NSLOT = 20 };
+       WS_VGEN = 19,
+       // the posterior pass (segment products and seeds): a slot of its own, so that it may run
+       // beside the E-step and the Viterbi on other streams
+       WS_POST = 20, WS_NSLOT = 21 };
 
 }  // namespace cpg
 
@@ -274,6 +279,18 @@ hipError_t launch_train(const cpg_model& model, const uint32_t* packed, const ui
                         int64_t nchunks, int64_t chunk_len, unsigned long long* acc, double* out,
                         unsigned long long* cacc, int64_t* cout, hipStream_t s,
                         const double2* gtab);
+
+// posterior decoding (k_posterior.hip) over nchunks whole chunks of C positions (several chunks:
+// C a multiple of 4096): post (float per position), sign (maximum-posterior path) and loglik
+// (per chunk) may each be null; gtab: est_tables
+size_t posterior_ws_bytes(int64_t nchunks, int64_t C);
+hipError_t launch_posterior(const cpg_model& model, const double2* gtab, const uint32_t* packed,
+                            int64_t nchunks, int64_t C, void* ws, float* post, uint32_t* sign,
+                            double* loglik, hipStream_t s);
+// mean of post over the span of each of min(*count, cap) island records (device-side count)
+hipError_t launch_island_conf(const float* post, int64_t nchunks, int64_t C, int64_t first_chunk,
+                              const cpg_island* isl, const int64_t* count, int64_t cap,
+                              float* conf, uint32_t* status, hipStream_t s);
 
 // ragged contig batches (k_contigs.hip)
 size_t contigs_sort_ws_bytes(int64_t n);

@@ -172,6 +172,40 @@ def decode(ctx: Context, model: HmmModel, packed: torch.Tensor, nbases: int,
     return sign_out, score, out, count
 
 
+def posterior(ctx: Context, model: HmmModel, packed: torch.Tensor, nbases: int,
+              chunk_len: int = _lib.DECODE_CHUNK, post_out: torch.Tensor | None = None,
+              sign_out: torch.Tensor | None = None, loglik: torch.Tensor | None = None):
+    """Posterior decoding (cpg_posterior_d) of every whole chunk: (post float32 per base =
+    P(island state | chunk, model), sign int32 words = the maximum-posterior path, loglik
+    float64 per chunk).  Floats and sign words past the last whole chunk are not written."""
+    nch = nbases // chunk_len
+    dev = packed.device
+    if post_out is None:
+        post_out = torch.empty(max(nbases, 1) + 4, dtype=torch.float32, device=dev)
+    if sign_out is None:
+        sign_out = torch.empty(words32(nbases) + 4, dtype=torch.int32, device=dev)
+    if loglik is None:
+        loglik = torch.empty(max(nch, 1), dtype=torch.float64, device=dev)
+    m = model.to_struct()
+    check(lib.cpg_posterior_d(ctx.handle, ptr(m), _dp(packed), nbases, chunk_len, _dp(post_out),
+                              _dp(sign_out), _dp(loglik), _stream()))
+    return post_out, sign_out, loglik
+
+
+def island_confidence(ctx: Context, post: torch.Tensor, nbases: int, chunk_len: int,
+                      islands_out: torch.Tensor, count: torch.Tensor, first_chunk: int = 0,
+                      out: torch.Tensor | None = None):
+    """Mean of `post` over the span of each island record (cpg_island_confidence_d): float32
+    per record of islands_out ([cap, 32] uint8, as islands() / decode() return it); the record
+    count is read on the device.  Records past the count are not written."""
+    cap = islands_out.shape[0]
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.float32, device=post.device)
+    check(lib.cpg_island_confidence_d(ctx.handle, _dp(post), nbases, chunk_len, first_chunk,
+                                      _dp(islands_out), _dp(count), cap, _dp(out), _stream()))
+    return out
+
+
 def islands_to_numpy(out: torch.Tensor, count: torch.Tensor) -> np.ndarray:
     n = int(count.item())
     n = min(n, out.shape[0])

@@ -95,16 +95,17 @@ class Context:
     def sync(self, stream=None):
         check(lib.cpg_sync(self.handle, stream))
 
-    def reserve(self, nbases: int, general: bool = False, chunk_len: int | None = None):
+    def reserve(self, nbases: int, general: bool = False, chunk_len: int | None = None,
+                posterior: bool = False):
         """cpg_reserve_ex: size the workspace for inputs of up to nbases bases at every decode
         chunk length that is a multiple of 256 (general=True: also the general-model
-        Viterbi's, ~26 B per base); with chunk_len, cpg_reserve_chunk: for that one decode
-        chunk length only."""
+        Viterbi's, ~26 B per base; posterior=True: also the posterior pass's); with chunk_len,
+        cpg_reserve_chunk: for that one decode chunk length only."""
+        flags = (1 if general else 0) | (2 if posterior else 0)
         if chunk_len is None:
-            check(lib.cpg_reserve_ex(self.handle, int(nbases), 1 if general else 0))
+            check(lib.cpg_reserve_ex(self.handle, int(nbases), flags))
         else:
-            check(lib.cpg_reserve_chunk(self.handle, int(nbases), int(chunk_len),
-                                        1 if general else 0))
+            check(lib.cpg_reserve_chunk(self.handle, int(nbases), int(chunk_len), flags))
 
     def workspace_bytes(self) -> int:
         """cpg_workspace_bytes: device workspace held by the context."""
@@ -144,6 +145,22 @@ class HmmEvaluator:
         check(lib.cpg_decode_states(ctx.handle, ptr(m), ptr(obs) if len(obs) else None,
                                     len(obs), ptr(out)))
         return out[: len(obs)]
+
+    @staticmethod
+    def posterior(model: HmmModel, observations, ctx: Context | None = None):
+        """Posterior decoding of one observation array (cpg_posterior_states): (float32
+        P(island state) per observation, log P(observations | model)).  Validation and
+        exceptions as decode(): CpgInvalid on symbols outside 0..3 or an empty array."""
+        obs = np.ascontiguousarray(observations, dtype=np.int32)
+        if obs.ndim != 1:
+            raise CpgInvalid(_lib.CPG_E_INVALID, "observations must be 1-D")
+        ctx = ctx or default_context()
+        out = np.zeros(max(len(obs), 1), np.float32)
+        ll = C.c_double(0.0)
+        m = model.to_struct()
+        check(lib.cpg_posterior_states(ctx.handle, ptr(m), ptr(obs) if len(obs) else None,
+                                       len(obs), ptr(out), C.byref(ll)))
+        return out[: len(obs)], ll.value
 
 
 def format_islands(records) -> bytes:

@@ -121,6 +121,9 @@ int         cpg_abi_version(void);
  * with cpg_reserve_ex(ctx, nbases, CPG_RESERVE_GENERAL). */
 int         cpg_reserve(cpg_ctx* ctx, int64_t nbases);
 #define CPG_RESERVE_GENERAL 1   /* also size the general-model Viterbi's workspace */
+#define CPG_RESERVE_POSTERIOR 2 /* also size the posterior pass's workspace (cpg_posterior_d:
+                                   chunk lengths that are multiples of 4096, and the whole
+                                   input as one chunk) */
 int         cpg_reserve_ex(cpg_ctx* ctx, int64_t nbases, int flags);
 /* As cpg_reserve_ex, for decode / island calls with this one chunk_len (a multiple of 32;
  * > 1 chunk per call needs a multiple of 256 for the Viterbi) and the training chunk
@@ -131,7 +134,7 @@ int         cpg_reserve_chunk(cpg_ctx* ctx, int64_t nbases, int64_t chunk_len, i
 int         cpg_workspace_bytes(cpg_ctx* ctx, int64_t* bytes);
 /* Wait for `stream` and return the first kernel-reported status since the last
  * cpg_sync: CPG_OK; CPG_E_VERIFY (a Viterbi exactness self-check failed); CPG_E_INVALID
- * (a broken contig layout); CPG_E_UNSUPPORTED (a general-model path not representable as
+ * (a broken contig layout, an island-confidence record outside its buffer); CPG_E_UNSUPPORTED (a general-model path not representable as
  * sign bits); CPG_E_DEVICE (the device reader, cpg_ingest_d).  No kernel of the decode /
  * island entry points waits for another workgroup.  The outputs of cpg_viterbi_d /
  * cpg_decode_d / cpg_islands_d are valid only once cpg_sync has returned CPG_OK for them. */
@@ -288,6 +291,39 @@ int cpg_decode_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* d_packed,
                  double* d_score, cpg_island* d_out, int64_t cap, int64_t* d_count,
                  void* stream);
 
+/* Posterior decoding (build-defined: the reference decodes with Viterbi only, :260) of every
+ * whole chunk_len chunk, each an independent observation sequence as in cpg_bw_estep_d: the
+ * forward-backward posteriors of the E-step kept per position instead of summed.  Outputs,
+ * each optional (NULL: not produced; all three NULL: a no-op returning CPG_OK):
+ *   d_post     : float32 per base, P(state in {A+,C+,G+,T+} | the whole chunk, model), the
+ *                fp64 posterior rounded once; floats past the last whole chunk are not written
+ *   d_sign_out : the maximum-posterior path as sign bits: 1 iff alpha+ beta+ > alpha- beta- in
+ *                fp64 (strict: a tie reads '-'); feeds cpg_islands_d unchanged.  Bits of the
+ *                last word past a chunk's end are 0; words past the last whole chunk are not
+ *                written
+ *   d_loglik   : fp64 log P(chunk | model) per chunk
+ * chunk_len: a multiple of 4096, at most 1048576, when there is more than one chunk; a single
+ * chunk may have any length >= 1.  d_post and d_sign_out: 16-byte aligned.
+ * Models: as cpg_bw_estep_d (deterministic emission rows, else CPG_E_UNSUPPORTED).  A chunk
+ * with P(chunk | model) = 0 (both live states of its first base at pi = 0) gets d_loglik =
+ * -inf, posteriors 0.0f and sign bits 0: no NaN, no error status.  Deterministic (bitwise
+ * reproducible).  Its workspace is its own (CPG_RESERVE_POSTERIOR sizes it): it may run
+ * beside the E-step and the Viterbi on other streams. */
+int cpg_posterior_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* d_packed,
+                    int64_t nbases, int64_t chunk_len, float* d_post, uint32_t* d_sign_out,
+                    double* d_loglik, void* stream);
+
+/* Island confidence: d_conf[i] = the mean of d_post (cpg_posterior_d's, over the same nbases /
+ * chunk_len) over the span of record i, for the first min(*d_count, cap) records of d_islands
+ * (the count is read on the device: no host synchronisation).  The span is recovered from the
+ * record: chunk-local start = (uint32)(beg1 - 1) - (uint32)chunk * (uint32)chunk_len (the
+ * int32-wrapped coordinates unwrap modulo 2^32), length = len, buffer chunk = chunk -
+ * first_chunk.  fp64 sums, stored as float32.  A record whose chunk or span falls outside the
+ * buffer gets NaN and cpg_sync reports CPG_E_INVALID. */
+int cpg_island_confidence_d(cpg_ctx* ctx, const float* d_post, int64_t nbases, int64_t chunk_len,
+                            int64_t first_chunk, const cpg_island* d_islands,
+                            const int64_t* d_count, int64_t cap, float* d_conf, void* stream);
+
 /* Device-side ASCII ingest: the reference's readers (CpGIslandFinder.java:112-145, mode 0 =
  * training; :238-259, mode 1 = decode) over raw text already in HBM, with exactly the
  * semantics of cpg_ingest (same quirks, same committed prefix, same error rules).  d_txt:
@@ -384,6 +420,12 @@ int cpg_viterbi(cpg_ctx* ctx, const cpg_model* model, const uint32_t* packed,
  * states_out[i] in 0..7. */
 int cpg_decode_states(cpg_ctx* ctx, const cpg_model* model, const int32_t* obs,
                       int64_t n, int32_t* states_out);
+/* cpg_posterior_d for one observation array (the counterpart of cpg_decode_states): obs[i] in
+ * 0..3 (else CPG_E_INVALID), n >= 1, the array being one chunk.  post_out: n floats, loglik:
+ * one double (either may be NULL, not both).  Staged through the context's pinned buffers:
+ * the caller's memory is never page-locked. */
+int cpg_posterior_states(cpg_ctx* ctx, const cpg_model* model, const int32_t* obs, int64_t n,
+                         float* post_out, double* loglik);
 /* cpg_ingest computed on the GPU: host text staged through pinned memory, the packed
  * chunks copied back.  Same arguments, results and return codes as cpg_ingest. */
 int cpg_ingest_gpu(cpg_ctx* ctx, const char* txt, size_t n, int mode, int compat_quirks,
