@@ -96,6 +96,8 @@ SIGNATURES = {
     "cpg_contigs_estep_d": [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P],
     "cpg_contigs_viterbi_d": [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P],
     "cpg_contigs_islands_d": [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P],
+    "cpg_contigs_posterior_d": [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P],
+    "cpg_contigs_island_confidence_d": [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P],
 }
 
 # test hooks exported by libcpg.so outside the C-ABI (cpg_internal.h): the readers started

@@ -334,7 +334,7 @@ int cpg_sync(cpg_ctx* ctx, void* stream) {
         if (st == ST_CONTIG_LAYOUT)
             return set_error(CPG_E_INVALID,
                              "contig batch: a contig breaks the layout contract (offset %% 64, "
-                             "length >= 1 (<= 2^20 for the E-step), inside nbases); skipped");
+                             "length >= 1 (<= 2^20 for the E-step and the posterior), inside nbases); skipped");
         return set_error(CPG_E_VERIFY,
                          "kernel self-check failed (status 0x%x: %s%s%s%s)", st,
                          (st & ST_VERIFY_ENTRY) ? "viterbi block exit != next entry; " : "",

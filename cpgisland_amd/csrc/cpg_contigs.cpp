@@ -98,6 +98,48 @@ int cpg_contigs_viterbi_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* 
     return CPG_OK;
 }
 
+int cpg_contigs_posterior_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* d_packed,
+                            int64_t nbases, const int64_t* d_offs, const int32_t* d_lens,
+                            const int32_t* d_order, int64_t n, float* d_post,
+                            uint32_t* d_sign_out, double* d_loglik, void* stream) {
+    int rc = check_batch(ctx, d_packed, nbases, d_offs, d_lens, n);
+    if (rc) return rc;
+    if (!model) return set_error(CPG_E_INVALID, "null argument");
+    if ((rc = model_check_deterministic(model))) return rc;
+    if (!aligned16(d_post) || !aligned16(d_sign_out))
+        return set_error(CPG_E_INVALID, "post / sign_out not 16-byte aligned");
+    if (n == 0 || (!d_post && !d_sign_out && !d_loglik)) return CPG_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CPG_HIP(hipSetDevice(ctx->device));
+    void* ck = nullptr;
+    // alpha checkpoints: 16 B per 64 bases of the packed span (the log-likelihoods alone are
+    // the forward pass: none)
+    if ((d_post || d_sign_out) &&
+        (rc = ws_get(ctx, WS_CPOST, (size_t)((nbases + 63) / 64) * 16 + 64, &ck)))
+        return rc;
+    CPG_HIP(launch_contigs_posterior(*model, d_packed, nbases, d_offs, d_lens, d_order, n, ck,
+                                     d_post, d_sign_out, d_loglik, ctx->d_status,
+                                     static_cast<hipStream_t>(stream)));
+    return CPG_OK;
+}
+
+int cpg_contigs_island_confidence_d(cpg_ctx* ctx, const float* d_post, int64_t nbases,
+                                    const int64_t* d_offs, const int32_t* d_lens, int64_t n,
+                                    const cpg_island* d_islands, const int64_t* d_count,
+                                    int64_t cap, float* d_conf, void* stream) {
+    if (!ctx || !d_count || cap < 0 || (cap > 0 && (!d_islands || !d_conf)) ||
+        (n > 0 && (!d_post || !d_offs || !d_lens)))
+        return set_error(CPG_E_INVALID, "null argument");
+    if (n < 0 || nbases < 0 || n >= (1ll << 31))
+        return set_error(CPG_E_INVALID, "contig batch: n=%lld nbases=%lld", (long long)n,
+                         (long long)nbases);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CPG_HIP(hipSetDevice(ctx->device));
+    CPG_HIP(launch_contigs_island_conf(d_post, nbases, d_offs, d_lens, n, d_islands, d_count, cap,
+                                       d_conf, ctx->d_status, static_cast<hipStream_t>(stream)));
+    return CPG_OK;
+}
+
 int cpg_contigs_islands_d(cpg_ctx* ctx, const uint32_t* d_packed, const uint32_t* d_sign,
                           int64_t nbases, const int64_t* d_offs, const int32_t* d_lens,
                           const int32_t* d_order, int64_t n, cpg_island* d_out, int64_t cap,

@@ -156,7 +156,9 @@ enum { WS_COUNT = 0, WS_VIT = 1, WS_ISL = 2, WS_EST = 3, WS_IN0 = 4, WS_IN1 = 5,
        WS_VGEN = 19,
        // the posterior pass (segment products and seeds): a slot of its own, so that it may run
        // beside the E-step and the Viterbi on other streams
-       WS_POST = 20, WS_NSLOT = 21 };
+       WS_POST = 20,
+       // the contig posterior's alpha checkpoints: its own, beside the contig E-step's WS_CCK
+       WS_CPOST = 21, WS_NSLOT = 22 };
 
 }  // namespace cpg
 
@@ -312,6 +314,19 @@ hipError_t launch_contigs_islands(const uint32_t* packed, const uint32_t* sign, 
                                   const int64_t* offs, const int32_t* lens, const int32_t* order,
                                   int64_t n, void* ws, size_t ws_bytes, cpg_island* out,
                                   int64_t cap, int64_t* count, uint32_t* status, hipStream_t s);
+// posterior decoding per contig (each <= 2^20 bases): post (float per base of the packed span),
+// sign_out (maximum-posterior path) and loglik (per contig) may each be null; ck: 16 B per 64
+// bases of the packed span (not needed for loglik alone)
+hipError_t launch_contigs_posterior(const cpg_model& model, const uint32_t* packed,
+                                    int64_t nbases, const int64_t* offs, const int32_t* lens,
+                                    const int32_t* order, int64_t n, void* ck, float* post,
+                                    uint32_t* sign_out, double* loglik, uint32_t* status,
+                                    hipStream_t s);
+// mean of post over the span of each of min(*count, cap) contig island records
+hipError_t launch_contigs_island_conf(const float* post, int64_t nbases, const int64_t* offs,
+                                      const int32_t* lens, int64_t n, const cpg_island* isl,
+                                      const int64_t* count, int64_t cap, float* conf,
+                                      uint32_t* status, hipStream_t s);
 
 // count0: the Java `count` before the first byte (0; the test hooks below: a chunk multiple)
 hipError_t launch_ingest(const uint8_t* txt, int64_t n, int mode, int quirks, int64_t chunk,

@@ -23,6 +23,9 @@
 //                       posteriors in unsigned fixed point 2^-38 into per-wave replicated LDS
 //                       bins (integer atomics: exact, order-independent), flushed to the same
 //                       128-bit accumulators the chunk E-step uses (finalized by k_estep_final);
+//   * posterior       : the E-step's walk emitting per position instead of summing: float32
+//                       P('+' | contig, model) per base, the maximum-posterior path as sign bits
+//                       and the contig log-likelihood; and the mean posterior of island records;
 //   * islands         : the :262-339 scan per lane with 32-position word fast paths (whole
 //                       background words skipped; whole island words by popcounts), two passes
 //                       around a device scan so records come out in contig order.
@@ -474,6 +477,248 @@ __global__ __launch_bounds__(kCT, kCtgEstWaves) void k_ctg_estep(Ctg a, cpg_mode
     }
 }
 
+// ------------------------------------------------------------------ posterior
+// The E-step's walk, emitting per position instead of summing: the same forward pass (alpha
+// checkpoints per 64-block in a scratch of its own), then per 64-block, last to first, the
+// alpha window of a 16-position mini-block in registers and beta walked backward;
+//   p+ = alpha+ beta+ / (alpha+ beta+ + alpha- beta-)   (any per-position scale cancels),
+// fp64, rounded once to float32; bit = alpha+ beta+ > alpha- beta- (strict: a tie reads '-').
+// The 64 lanes of a wave are on 64 contigs: nothing coalesces across lanes, so a mini-block's
+// 16 floats stay in registers and leave as four 16-B stores, a block's two sign words as one
+// 8-B store.  Floats and bits of the last block past the contig's end are written as 0.
+// kPost = false: no division, conversion or float stores (the path alone); kBack = false: the
+// forward pass alone (log-likelihoods), no checkpoints.
+// The division is a true fp64 division: the denominator may be denormal (pi = 1e-300 at a
+// contig's first positions, before the first rescaling), where rcp_nr's v_rcp_f64 is not
+// defined.  (rcp_nr of the denominator scaled to [0.5, 1) by its own exponent was measured:
+// the same time with all outputs, 45.8 against 45.9 ms on 1M contigs: the float stores bound
+// that form)  A zero denominator is a contig with P(contig | model) = 0: 0.0f,
+// bit 0.
+constexpr int kCtgPostWaves = 3;   // min waves per SIMD, as the E-step (VGPR budget 512 / this)
+template <bool kPost, bool kBack>
+__global__ __launch_bounds__(kCT, kCtgPostWaves) void k_ctg_posterior(
+    Ctg a, cpg_model model, double2* __restrict__ ck, float* __restrict__ post,
+    uint32_t* __restrict__ sign_out, double* __restrict__ loglik) {
+// a tolerance-bound fp64 computation: products and sums may contract to FMAs
+#pragma clang fp contract(fast)
+    __shared__ double2 TA[16], TB[16];   // rows of M_d: (M(+,+), M(+,-)), (M(-,+), M(-,-))
+    __shared__ double2 sent[3][kCT];     // alpha entering mini-blocks 1..3, per lane
+    const int t = threadIdx.x;
+    if (t < 16) {
+        const int p = t & 3, b = t >> 2;
+        TA[t] = make_double2(model.a[p][b], model.a[p][b + 4]);
+        TB[t] = make_double2(model.a[p + 4][b], model.a[p + 4][b + 4]);
+    }
+    __syncthreads();
+    const uint4* pk4 = reinterpret_cast<const uint4*>(a.packed);
+    uint2* so2 = reinterpret_cast<uint2*>(sign_out);
+    const int64_t stride = (int64_t)gridDim.x * kCT;
+    // (no barrier in the loop: a lane reads only its own column of sent)
+    for (int64_t g = (int64_t)blockIdx.x * kCT + t; g < a.n; g += stride) {
+        int64_t c, off, len;
+        if (!ctg_get(a, g, c, off, len, 1 << 20)) continue;
+        const int64_t nblk = (len + 63) / 64, b0 = off / 64;
+        const uint32_t o0 = a.packed[off / 16] & 3u;
+        // forward: alpha with power-of-two rescaling, checkpoints at every block start
+        double aP = model.pi[o0], aM = model.pi[o0 + 4];
+        int64_t E = 0;
+        uint32_t prev = o0;
+        for (int64_t i = 0; i < nblk; ++i) {
+            if (kBack && i > 0) ck[b0 + i] = make_double2(aP, aM);   // alpha at position 64 i - 1
+            const uint4 w = pk4[b0 + i];
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+            const int64_t left = len - 64 * i;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+#pragma unroll 4
+                for (int j = 0; j < 16; ++j) {
+                    const int p = 16 * k + j;
+                    if (p >= left) break;
+                    const uint32_t cur = (ww[k] >> (2 * j)) & 3u;
+                    if (i > 0 || p > 0) {
+                        const double2 ma = TA[prev | (cur << 2)], mb = TB[prev | (cur << 2)];
+                        const double nP = aP * ma.x + aM * mb.x, nM = aP * ma.y + aM * mb.y;
+                        aP = nP;
+                        aM = nM;
+                        if ((j & 3) == 3) E += vnorm(aP, aM);
+                    }
+                    prev = cur;
+                }
+            }
+        }
+        // P(contig | model) = 0 (both live states of the first base at pi = 0): log 0 = -inf
+        if (loglik) loglik[c] = log(aP + aM) + (double)E * 0.69314718055994530942;
+        if (!kBack) continue;
+        // backward, last block first; beta at the last position = (1, 1)
+        double yP = 1.0, yM = 1.0;
+        for (int64_t i = nblk - 1; i >= 0; --i) {
+            const uint4 w = pk4[b0 + i];
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+            const uint32_t wprev = i > 0 ? a.packed[off / 16 + 4 * i - 1] : 0u;
+            const int64_t left = len - 64 * i;
+            // alpha entering the block (position 64 i - 1) and, in LDS, entering its
+            // mini-blocks 1..3 (positions 16 k - 1): registers stay for the alpha window
+            double xP0, xM0;
+            if (i > 0) {
+                const double2 e = ck[b0 + i];
+                xP0 = e.x;
+                xM0 = e.y;
+            } else {
+                xP0 = model.pi[o0];
+                xM0 = model.pi[o0 + 4];
+            }
+            {
+                double xP = xP0, xM = xM0;
+                uint32_t pv = wprev >> 30;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+#pragma unroll 4
+                    for (int j = 0; j < 16; ++j) {
+                        const uint32_t cur = (ww[k] >> (2 * j)) & 3u;
+                        if (16 * k + j < left && (i > 0 || k > 0 || j > 0)) {
+                            const double2 ma = TA[pv | (cur << 2)], mb = TB[pv | (cur << 2)];
+                            const double nP = xP * ma.x + xM * mb.x, nM = xP * ma.y + xM * mb.y;
+                            xP = nP;
+                            xM = nM;
+                            if ((j & 3) == 3) vnorm(xP, xM);
+                        }
+                        pv = cur;
+                    }
+                    sent[k][t] = make_double2(xP, xM);
+                }
+            }
+            float* pblk = kPost ? post + off + 64 * i : nullptr;
+            uint32_t sw0 = 0u, sw1 = 0u;   // the block's sign words
+#pragma unroll 1
+            for (int k = 3; k >= 0; --k) {
+                if (16 * k >= left) {   // wholly past the contig's end: zeros
+                    if (kPost) {
+                        float4* o = reinterpret_cast<float4*>(pblk + 16 * k);
+                        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        o[0] = z;
+                        o[1] = z;
+                        o[2] = z;
+                        o[3] = z;
+                    }
+                    continue;
+                }
+                // the mini-block's word and the base before it (select chains: no
+                // register indexing)
+                const uint32_t wk = k == 0 ? ww[0] : k == 1 ? ww[1] : k == 2 ? ww[2] : ww[3];
+                const uint32_t pk = (k == 0 ? wprev : k == 1 ? ww[0] : k == 2 ? ww[1] : ww[2]) >> 30;
+                double eP = xP0, eM = xM0;
+                if (k > 0) {
+                    const double2 e = sent[k - 1][t];
+                    eP = e.x;
+                    eM = e.y;
+                }
+                // alpha at the 16 positions of the mini-block (registers)
+                double alP[16], alM[16];
+                {
+                    double xP = eP, xM = eM;
+                    uint32_t pv = pk;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const uint32_t cur = (wk >> (2 * j)) & 3u;
+                        if (16 * k + j < left && (i > 0 || k > 0 || j > 0)) {
+                            const double2 ma = TA[pv | (cur << 2)], mb = TB[pv | (cur << 2)];
+                            const double nP = xP * ma.x + xM * mb.x, nM = xP * ma.y + xM * mb.y;
+                            xP = nP;
+                            xM = nM;
+                            if ((j & 3) == 3) vnorm(xP, xM);
+                        }
+                        alP[j] = xP;
+                        alM[j] = xM;
+                        pv = cur;
+                    }
+                }
+                float pf[16];
+                uint32_t bits = 0u;
+#pragma unroll
+                for (int j = 15; j >= 0; --j) {
+                    const int p = 16 * k + j;
+                    if (p >= left) {
+                        if (kPost) pf[j] = 0.0f;
+                        continue;
+                    }
+                    const double qP = alP[j] * yP, qM = alM[j] * yM;
+                    bits |= qP > qM ? (1u << j) : 0u;
+                    if (kPost) {
+                        const double den = qP + qM;
+                        pf[j] = den > 0.0 ? (float)(qP / den) : 0.0f;
+                    }
+                    if (i == 0 && p == 0) continue;   // no transition into position 0
+                    const uint32_t d = (j > 0 ? ((wk >> (2 * j - 2)) & 3u) : pk) |
+                                       (((wk >> (2 * j)) & 3u) << 2);
+                    const double2 ma = TA[d], mb = TB[d];
+                    const double nP = ma.x * yP + ma.y * yM, nM = mb.x * yP + mb.y * yM;
+                    yP = nP;
+                    yM = nM;
+                    if ((j & 3) == 0) vnorm(yP, yM);
+                }
+                if (kPost) {
+                    float4* o = reinterpret_cast<float4*>(pblk + 16 * k);
+                    o[0] = make_float4(pf[0], pf[1], pf[2], pf[3]);
+                    o[1] = make_float4(pf[4], pf[5], pf[6], pf[7]);
+                    o[2] = make_float4(pf[8], pf[9], pf[10], pf[11]);
+                    o[3] = make_float4(pf[12], pf[13], pf[14], pf[15]);
+                }
+                const uint32_t sh = bits << (16 * (k & 1));
+                if (k & 2)
+                    sw1 |= sh;
+                else
+                    sw0 |= sh;
+            }
+            if (sign_out) so2[b0 + i] = make_uint2(sw0, sw1);
+        }
+    }
+}
+
+// Contig island confidence: one wave per record, the mean of post over the record's span.
+// Contig c = rec.chunk, span = [offs[c] + beg1 - 1, + len): contig records carry the contig
+// index and contig-local coordinates (k_ctg_islands).  A record whose contig is outside
+// [0, n), or whose span is not inside the contig (or the contig not inside the buffer): NaN
+// and the status bit.  The reduction is k_island_conf's (fp64, fixed order).
+__global__ __launch_bounds__(256) void k_ctg_island_conf(const float* __restrict__ post,
+                                                         int64_t nbases,
+                                                         const int64_t* __restrict__ offs,
+                                                         const int32_t* __restrict__ lens,
+                                                         int64_t n,
+                                                         const cpg_island* __restrict__ isl,
+                                                         const int64_t* __restrict__ d_count,
+                                                         int64_t cap, float* __restrict__ conf,
+                                                         uint32_t* __restrict__ status) {
+    int64_t nrec = *d_count;
+    nrec = nrec < 0 ? 0 : (nrec > cap ? cap : nrec);
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < nrec;
+         i += nwaves) {
+        const cpg_island r = isl[i];
+        const int64_t c = r.chunk, start = (int64_t)r.beg1 - 1;
+        bool ok = c >= 0 && c < n && r.len >= 1 && start >= 0;
+        int64_t off = 0;
+        if (ok) {
+            off = offs[c];
+            const int64_t L = lens[c];
+            ok = start + r.len <= L && off >= 0 && off + L <= nbases;
+        }
+        if (!ok) {
+            if (lane == 0) {
+                conf[i] = __builtin_nanf("");
+                atomicOr(status, (uint32_t)ST_CONF_RANGE);
+            }
+            continue;
+        }
+        const float* p = post + off + start;
+        double s = 0.0;
+        for (int k = lane; k < r.len; k += 64) s += (double)p[k];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);   // fixed order
+        if (lane == 0) conf[i] = (float)(s / (double)r.len);
+    }
+}
+
 // ------------------------------------------------------------------ islands
 struct IslState {
     bool in;
@@ -703,6 +948,39 @@ hipError_t launch_contigs_estep(const cpg_model& model, const uint32_t* packed, 
                            make_ctg(packed, nullptr, nbases, offs, lens, order, n, status), model,
                            static_cast<double2*>(ck), acc);
     return launch_estep(model, nullptr, 0, CPG_TRAIN_CHUNK, acc, out, s, PART_FINAL);
+}
+
+hipError_t launch_contigs_posterior(const cpg_model& model, const uint32_t* packed,
+                                    int64_t nbases, const int64_t* offs, const int32_t* lens,
+                                    const int32_t* order, int64_t n, void* ck, float* post,
+                                    uint32_t* sign_out, double* loglik, uint32_t* status,
+                                    hipStream_t s) {
+    if (n <= 0 || (!post && !sign_out && !loglik)) return hipSuccess;
+    if ((post || sign_out) && !ck) return hipErrorInvalidValue;
+    const Ctg a = make_ctg(packed, nullptr, nbases, offs, lens, order, n, status);
+    double2* c2 = static_cast<double2*>(ck);
+    const dim3 grid(grid_for(n)), block(kCT);
+    if (post)
+        hipLaunchKernelGGL((k_ctg_posterior<true, true>), grid, block, 0, s, a, model, c2, post,
+                           sign_out, loglik);
+    else if (sign_out)
+        hipLaunchKernelGGL((k_ctg_posterior<false, true>), grid, block, 0, s, a, model, c2, post,
+                           sign_out, loglik);
+    else
+        hipLaunchKernelGGL((k_ctg_posterior<false, false>), grid, block, 0, s, a, model, c2, post,
+                           sign_out, loglik);
+    return hipGetLastError();
+}
+
+hipError_t launch_contigs_island_conf(const float* post, int64_t nbases, const int64_t* offs,
+                                      const int32_t* lens, int64_t n, const cpg_island* isl,
+                                      const int64_t* count, int64_t cap, float* conf,
+                                      uint32_t* status, hipStream_t s) {
+    if (cap <= 0) return hipSuccess;
+    const int64_t blocks = (cap + 3) / 4;   // 4 waves per workgroup, one record per wave and turn
+    hipLaunchKernelGGL(k_ctg_island_conf, dim3((unsigned)(blocks < 2048 ? blocks : 2048)),
+                       dim3(256), 0, s, post, nbases, offs, lens, n, isl, count, cap, conf, status);
+    return hipGetLastError();
 }
 
 hipError_t launch_contigs_islands(const uint32_t* packed, const uint32_t* sign, int64_t nbases,

@@ -347,3 +347,42 @@ def contigs_islands(ctx, packed, sign, nbases, offs, lens, order, n, cap=1 << 20
                                     _dp(lens), _opt(order), n, _dp(out), cap, _dp(count),
                                     _stream()))
     return out, count
+
+
+def contigs_posterior(ctx, model: HmmModel, packed, nbases, offs, lens, order, n,
+                      want_post=True, want_sign=True, want_loglik=True,
+                      post_out=None, sign_out=None, loglik=None):
+    """Posterior decoding per contig (cpg_contigs_posterior_d): (post float32 per base of the
+    packed span at offs[c] + p, sign int32 words = the maximum-posterior path shaped as
+    contigs_viterbi()'s, loglik float64 per contig).  An output that is not wanted (want_* False
+    and no buffer given) is not computed and returned as None.  Floats and sign words outside
+    the contigs' own 64-base blocks are not written (fresh buffers: post NaN, sign 0)."""
+    dev = packed.device
+    if post_out is None and want_post:
+        post_out = torch.full(((nbases + 63) // 64 * 64 + 64,), float("nan"),
+                              dtype=torch.float32, device=dev)
+    if sign_out is None and want_sign:
+        sign_out = torch.zeros(words32(nbases) + 4, dtype=torch.int32, device=dev)
+    if loglik is None and want_loglik:
+        loglik = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    m = model.to_struct()
+    check(lib.cpg_contigs_posterior_d(ctx.handle, ptr(m), _dp(packed), nbases, _dp(offs),
+                                      _dp(lens), _opt(order), n, _opt(post_out), _opt(sign_out),
+                                      _opt(loglik), _stream()))
+    return post_out, sign_out, loglik
+
+
+def contigs_island_confidence(ctx, post, nbases, offs, lens, n, islands, count, cap=None,
+                              out=None):
+    """Mean of `post` (contigs_posterior()'s) over the span of each contig island record
+    (cpg_contigs_island_confidence_d): float32 per record of `islands` ([cap, 32] uint8, as
+    contigs_islands() returns it); the record count is read on the device.  Records past the
+    count are not written."""
+    if cap is None:
+        cap = islands.shape[0]
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.float32, device=post.device)
+    check(lib.cpg_contigs_island_confidence_d(ctx.handle, _dp(post), nbases, _dp(offs), _dp(lens),
+                                              n, _dp(islands), _dp(count), cap, _dp(out),
+                                              _stream()))
+    return out

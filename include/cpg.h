@@ -379,6 +379,40 @@ int cpg_contigs_islands_d(cpg_ctx* ctx, const uint32_t* d_packed, const uint32_t
                           int64_t nbases, const int64_t* d_offs, const int32_t* d_lens,
                           const int32_t* d_order, int64_t n, cpg_island* d_out, int64_t cap,
                           int64_t* d_count, void* stream);
+/* Posterior decoding per contig (build-defined, as cpg_posterior_d with the contig as the
+ * chunk): batch layout, d_order and the model (deterministic emission rows, else
+ * CPG_E_UNSUPPORTED) as cpg_contigs_estep_d; each contig <= 1,048,576 bases (a longer one is
+ * skipped and cpg_sync reports CPG_E_INVALID: longer sequences go through cpg_posterior_d as a
+ * single chunk).  Outputs, each optional (NULL: not produced; all three NULL, or n == 0: a
+ * no-op returning CPG_OK):
+ *   d_post     : float32 per base of the packed span, P(state in {A+,C+,G+,T+} | the whole
+ *                contig, model) at d_post[offs[c] + p], the fp64 posterior rounded once;
+ *                capacity nbases rounded up to 64 floats, 16-byte aligned.  The floats between
+ *                a contig's end and the end of its last 64-base block are written as 0.0f; all
+ *                others (gaps between contigs, skipped contigs) are not written
+ *   d_sign_out : the maximum-posterior path as sign bits (1 iff alpha+ beta+ > alpha- beta- in
+ *                fp64, strict: a tie reads '-'), shaped and aligned as cpg_contigs_viterbi_d's;
+ *                feeds cpg_contigs_islands_d unchanged.  Only the words of the contigs' own
+ *                64-base blocks are written; bits past a contig's end are 0
+ *   d_loglik   : fp64 log P(contig | model) in d_loglik[c], n doubles
+ * A contig with P(contig | model) = 0 (both live states of its first base at pi = 0) gets
+ * d_loglik = -inf, posteriors 0.0f and sign bits 0: no NaN, no error status.  Results never
+ * depend on d_order and are bitwise reproducible.  Its scratch is its own: it may run beside
+ * cpg_contigs_estep_d on another stream. */
+int cpg_contigs_posterior_d(cpg_ctx* ctx, const cpg_model* model, const uint32_t* d_packed,
+                            int64_t nbases, const int64_t* d_offs, const int32_t* d_lens,
+                            const int32_t* d_order, int64_t n, float* d_post,
+                            uint32_t* d_sign_out, double* d_loglik, void* stream);
+/* Island confidence for contig records (cpg_contigs_islands_d's: `chunk` = contig index, beg1
+ * 1-based within the contig): d_conf[i] = the mean of d_post (cpg_contigs_posterior_d's, over
+ * the same batch) over bases [offs[c] + beg1 - 1, + len) of contig c = chunk, for the first
+ * min(*d_count, cap) records (the count is read on the device).  fp64 sums, stored as float32.
+ * A record whose contig index is outside [0, n), or whose span is not inside its contig, gets
+ * NaN and cpg_sync reports CPG_E_INVALID. */
+int cpg_contigs_island_confidence_d(cpg_ctx* ctx, const float* d_post, int64_t nbases,
+                                    const int64_t* d_offs, const int32_t* d_lens, int64_t n,
+                                    const cpg_island* d_islands, const int64_t* d_count,
+                                    int64_t cap, float* d_conf, void* stream);
 
 /* ---- streamed whole-genome pass (host memory -> HBM, overlapped) ---------------- */
 /* One training + decode pass over a genome in HOST memory, streamed to the device in windows
